@@ -14,7 +14,13 @@ library's RCCL all-gather of C (lamm_hip_allgather_rows), so each rank holds the
 The K steps are captured once as a hipGraph and replayed (per-launch host submission through
 Python/ctypes costs ~5 us, more than the kernel; bench measures the GPU).
 
-Beside it (same JSON line):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only that: set-up, W warm-up steps, the
+K timed steps, and one JSON line with `value` and `ms_per_step` (wall milliseconds per timed step).
+`--dump-outputs DIR` also writes C as the last timed step left it to DIR/C.npy (float32, all M
+rows); every input is seeded, so two builds of the library can be compared output for output.
+
+With `--full`, beside it (same JSON line; the roofline above, the event-timed and direct-dispatch
+figures of the same steps, and):
   gemv_stacked  : 33 4096x4096 slices in ONE launch (steady-state streaming rate), N = 1
   gemm          : BASELINE config 3 (M=4096 N=512 K=4096, stationary weights): one slice and
                   a 4-slice batch; roofline = the WHOLE launch (activation prep + main loop +
@@ -25,7 +31,7 @@ Beside it (same JSON line):
   sweep         : BASELINE config 4 (Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K at K=4096): per format the
                   single-call GEMV (config 2's measurement) and the config-3-shaped GEMM
   llama7b_e2e   : BASELINE config 5 through the unchanged caller -- llama.cpp-b2430's own
-                  llama_decode (integration/_build/llama_e2e_hip: the reference's llama.cpp and
+                  llama_decode (oracle/_ref/llama_e2e_hip: the reference's llama.cpp and
                   ggml with the LA_LLAMA hook linked to liblamm_hip.so), synthetic Llama-7B Q4_0
                   GGUF, pp512 / tg128; with N GPUs the boundary splits every weight's rows over
                   all N (LAMM_HIP_DEVICES)
@@ -194,12 +200,13 @@ def flush_caches(torch):
     _SCRATCH.fill_(1)
 
 
-def time_steps(ctx, step, steps, warmup, graph=True, flush=False):
+def time_steps(ctx, step, steps, warmup, graph=True, flush=False, events=True):
     """Warm-up, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides;
     returns (wall seconds per step, event-timed seconds per step -- both max over ranks --,
     graph used).  graph: the steps are captured once as a hipGraph and replayed in the timed
     region.  Everything runs on one side stream, the warm-up included, so the library's
-    per-stream workspaces exist before the capture (nothing allocates while capturing)."""
+    per-stream workspaces exist before the capture (nothing allocates while capturing).
+    events=False: the wall-clock pass alone (the event-timed figure is None)."""
     torch = ctx.torch
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
@@ -239,14 +246,17 @@ def time_steps(ctx, step, steps, warmup, graph=True, flush=False):
         torch.cuda.synchronize()
         ctx.barrier()
         wall = time.perf_counter() - t0
-        # the same K steps again, timed by HIP events on the stream they run on
-        if flush:
-            flush_caches(torch)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        run()
-        e1.record(st)
+        if events:
+            # the same K steps again, timed by HIP events on the stream they run on
+            if flush:
+                flush_caches(torch)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            run()
+            e1.record(st)
     torch.cuda.synchronize()
+    if not events:
+        return ctx.max(wall / steps)[0], None, g is not None
     ev = e0.elapsed_time(e1) / 1e3
     wmax, emax = ctx.max(wall / steps, ev / steps)
     return wmax, emax, g is not None
@@ -376,9 +386,12 @@ def time_direct(ctx, mats, R, Bm, Cm, steps, warmup, flags=0):
     return ctx.max(wall / steps, 0.0)[0]
 
 
-def config2_gemv(ctx, fmt, M, K, steps, warmup):
+def config2_gemv(ctx, fmt, M, K, steps, warmup, full_run=True):
     """BASELINE config 2, strong-scaled: rank r owns rows [r0, r0 + rows) of ONE M x K weight;
-    a step = its slab's GEMV on the next of R rotated weight copies + the RCCL all-gather of C."""
+    a step = its slab's GEMV on the next of R rotated weight copies + the RCCL all-gather of C.
+    full_run=False: the timed steps alone (per_step, and the gathered C of the last one as `output`);
+    the event-timed pass, the direct-dispatch run, the gather check, the parity sample and the
+    per-launch / floor measurements need full_run."""
     torch, la = ctx.torch, ctx.la
     t = la.BY_NAME[fmt]
     vt = la.vec_dot_type(t)
@@ -411,13 +424,19 @@ def config2_gemv(ctx, fmt, M, K, steps, warmup):
         gemv(i)
         ctx.allgather_rows(C, M, 1, ALIGN, torch.cuda.current_stream().cuda_stream)
 
-    per_step, ev_step, graphed = time_steps(ctx, step, steps, warmup, graph=not ctx.rehearse, flush=True)
-    # one GPU: the same K steps dispatched on the library's own AQL queue (no collective to order
-    # against), reported beside the graph replay as value_direct
-    direct = time_direct(ctx, mats, R, Bm, Cm, steps, warmup) if ctx.world == 1 else None
+    per_step, ev_step, graphed = time_steps(ctx, step, steps, warmup, graph=not ctx.rehearse, flush=True,
+                                            events=full_run)
     last = warmup + steps - 1
     torch.cuda.synchronize()
     gathered = C.clone()      # C after the last timed step (copy last % R)
+    if not full_run:
+        res = dict(per_step=per_step, graphed=graphed, R=R, rows=rows, output=gathered.cpu().numpy())
+        del A, B, C
+        torch.cuda.empty_cache()
+        return res
+    # one GPU: the same K steps dispatched on the library's own AQL queue (no collective to order
+    # against), reported beside the graph replay as value_direct
+    direct = time_direct(ctx, mats, R, Bm, Cm, steps, warmup) if ctx.world == 1 else None
     check = None
     if ctx.world > 1:
         # rank 0: the gathered C of the last step vs one GPU computing all rows of that copy
@@ -455,7 +474,7 @@ def config2_gemv(ctx, fmt, M, K, steps, warmup):
         kern_method = "HIP events over 1000 back-to-back hipGraph-replayed launches on their stream"
     res = dict(per_step=per_step, direct_step=direct, ev_step=ev_step, kern=kern,
                kern_method=kern_method, kern_b2b=b2b, floor=floor, empty=empty, graphed=graphed,
-               R=R, rows=rows,
+               R=R, rows=rows, output=gathered.cpu().numpy(),
                slab_bytes=slab_bytes + la.row_bytes(vt, K) + 4 * rows, gather_check=check, sample=sample)
     del A, B, C
     torch.cuda.empty_cache()
@@ -765,7 +784,7 @@ def parity_sample(samples):
 def llama_e2e(devices, n_prompt=512, n_gen=128, threads=16, exe=None, extra_env=None, timeout=600, keep_tokens=False,
               extra_args=()):
     """BASELINE config 5 through llama.cpp-b2430's own llama_decode (see module doc)."""
-    exe = exe or os.path.join(ROOT, "integration", "_build", "llama_e2e_hip")
+    exe = exe or os.path.join(ROOT, "oracle", "_ref", "llama_e2e_hip")
     model = os.path.join(os.environ.get("TMPDIR", "/tmp"), "lamm_synth_llama7b_q4_0.gguf")
     if not os.path.exists(exe):
         return {"error": f"{exe} missing (build with __graft_entry__.build())"}
@@ -822,7 +841,7 @@ def la_benchmark(dtype="q4_0", gpu_threads=4, iters=10):
     out = {"workload": f"la-benchmark-matmult -d {dtype} -i {iters}: ggml_mul_mat of ({dtype} 4096 x 11008) x (F32 11008 "
                        "x 128), ggml INIT quantization of src1 included, the binary's own Average GFLOPS"}
     cores = host_cores()[0]
-    for name, exe, th in (("gpu", os.path.join(ROOT, "integration", "_build", "la-benchmark-matmult_hip"), gpu_threads),
+    for name, exe, th in (("gpu", os.path.join(ROOT, "oracle", "_ref", "la-benchmark-matmult_hip"), gpu_threads),
                           ("cpu_reference", os.path.join(ROOT, "oracle", "_ref", "la-benchmark-matmult_lamm3"), cores)):
         if not os.path.exists(exe):
             out[name] = {"error": f"{exe} missing"}
@@ -911,6 +930,13 @@ def main():
     ap.add_argument("--M", type=int, default=4096)
     ap.add_argument("--K", type=int, default=4096)
     ap.add_argument("--gemm-N", type=int, default=512)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (config 2's C, float32) "
+                         "to DIR/C.npy; the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the event-timed, direct-dispatch and per-launch roofline figures, the "
+                         "other configurations / formats / kernels, config 5 and the CPU baselines with their parity "
+                         "checks (the --no-* / --sweep / --gemm-N / --cpu-budget options select among these)")
     ap.add_argument("--no-gemm", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-llama", action="store_true", help="skip config 5 (llama e2e + weight-matmul step)")
@@ -930,16 +956,12 @@ def main():
     M, K, fmt = args.M, args.K, args.fmt
     unit = gemv_bytes(la, fmt, M, K)
 
-    g = config2_gemv(ctx, fmt, M, K, args.steps, args.warmup)
+    g = config2_gemv(ctx, fmt, M, K, args.steps, args.warmup, full_run=args.full)
     value = unit / g["per_step"] / 1e9
-    achieved = g["slab_bytes"] / g["kern"] / 1e9
-    traffic = read_profile("traffic", f"{fmt}_gemv_single")
-    trace = read_profile("roofline", f"{fmt}_gemv_single")
-    kname = "gemv_flat1_kernel" if la.gemm_engine(fmt, g["rows"], 1, K) == "gemv" and K == 4096 else None
     out = {
         "metric": "Q4_0xQ8_0 GEMM effective GFLOPS @ K=4096; achieved HBM GB/s (GEMV)",
         "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(g["per_step"] * 1e3, 5), "gpu_ms_per_step": round(g["ev_step"] * 1e3, 5),
+        "ms_per_step": round(g["per_step"] * 1e3, 5),
         "higher_is_better": True, "scaling": "strong",
         "vs_baseline": None, "dtype": "i8",
         "data": "synthetic (random block bytes with valid fp16 scales; B = GPU q8 quantizer of N(0,1))",
@@ -952,6 +974,39 @@ def main():
                                   ((" + all-gather through gloo (one-GPU rehearsal)" if ctx.rehearse else
                                     " + lamm_hip_allgather_rows (RCCL)") if world > 1 else ""),
                    "timing": "hipGraph of the K steps, replayed" if g["graphed"] else "eager launches"},
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"C": g["output"]})
+    if args.full:
+        full_report(args, ctx, out, g)
+    ctx.close()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, one
+    <name>.npy per array (float32).  C: config 2's GEMV result, all M rows (gathered over the ranks)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def full_report(args, ctx, out, g):
+    """--full: everything beside the headline, added to `out` -- config 2's event-timed, direct-dispatch
+    and per-launch roofline figures, the other configurations, formats and kernels, config 5, and
+    the cpu_baseline leg with its parity checks (see the module doc)."""
+    la = ctx.la
+    world, rank = ctx.world, ctx.rank
+    M, K, fmt = args.M, args.K, args.fmt
+    unit = gemv_bytes(la, fmt, M, K)
+    achieved = g["slab_bytes"] / g["kern"] / 1e9
+    traffic = read_profile("traffic", f"{fmt}_gemv_single")
+    trace = read_profile("roofline", f"{fmt}_gemv_single")
+    kname = "gemv_flat1_kernel" if la.gemm_engine(fmt, g["rows"], 1, K) == "gemv" and K == 4096 else None
+    out.update({
+        "gpu_ms_per_step": round(g["ev_step"] * 1e3, 5),
         # the same K steps as K calls from C on the library's own AQL queue (lamm_hip_direct_begin /
         # end: one packet per call, one completion signal for the region), same brackets
         "value_direct": round(unit / g["direct_step"] / 1e9, 2) if g["direct_step"] else None,
@@ -976,7 +1031,7 @@ def main():
                      # an EMPTY kernel on the same grid, timed the same way: the dispatch's own cost
                      "empty_launch_us": round(g["empty"] * 1e6, 3) if g["empty"] else None,
                      "algorithmic_bytes_per_launch": g["slab_bytes"]},
-    }
+    })
     if trace and kname and trace.get("algorithmic_bytes_per_launch") == g["slab_bytes"]:
         # the kernel tracer's own durations of the same kernel, launched one at a time (the tracer
         # stretches back-to-back dispatches by its own per-dispatch cost)
@@ -1080,7 +1135,7 @@ def main():
         ctx.barrier()
         if rank == 0:
             devs = list(range(world)) if world > 1 and not ctx.rehearse else None
-            e2e = {"note": "BASELINE config 5: llama.cpp-b2430's own llama_decode (integration/_build/llama_e2e_hip: "
+            e2e = {"note": "BASELINE config 5: llama.cpp-b2430's own llama_decode (oracle/_ref/llama_e2e_hip: "
                            "the reference's llama.cpp + ggml, LA_LLAMA hook -> liblamm_hip.so), synthetic "
                            "Llama-7B-shaped Q4_0 GGUF (Q6_K output, F16 KV cache), pp512 then tg128 greedy behind the "
                            "prompt (tg_tok_s), and llama-bench's own tg128 from an empty cache "
@@ -1160,10 +1215,8 @@ def main():
             else:
                 par["error"] = c.get("error")
             out["llama7b_e2e"]["parity_32_layers"] = par
-    ctx.close()
     if rank == 0:
         out["summary"] = summary(out)   # last key: what a tail of the line keeps
-        print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

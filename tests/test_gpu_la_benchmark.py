@@ -1,9 +1,9 @@
 """The reference's OWN benchmark, unchanged, through the hook (north_star: "la-benchmark-matmult
 runs unchanged").
 
-`/root/reference/src/la-benchmark-matmult.cpp` is compiled as it lies (integration/Makefile:
-`la-benchmark-matmult_hip`, and `_hip_debug` = the reference's LAMM_DEBUG=1 build,
-/root/reference/Makefile:7-9) against the reference's unchanged ggml + llama objects, its
+The reference's `src/la-benchmark-matmult.cpp` is compiled as it lies (oracle/Makefile:
+`la-benchmark-matmult_hip`, and `_hip_debug` = the reference's LAMM_DEBUG=1 build, its top-level
+Makefile:7-9) against the reference's unchanged ggml + llama objects, its
 `#include "loongarch_matmul.h"` resolved to include/ and the hook to liblamm_hip.so -- the build
 LC/Makefile:863-867 makes, with our library in place of src/loongarch_matmul.o.  Each run is the
 reference's own test command (`/root/reference/test/utils.py:21-24`: `-d <type> -t N -i N`) and is
@@ -27,8 +27,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "integration", "_build")
 REF = os.path.join(ROOT, "oracle", "_ref")
+BUILD = REF
 # the reference test suite's own pattern (test/test_matmult_performance.py:42)
 AVERAGE = re.compile(r'\nAverage\s*(\d+\.\d+)\n')
 SUM = re.compile(r'Sum of tensor gf->nodes\[0\] is\s*(-?\d+\.\d+)')
@@ -40,7 +40,7 @@ ITERS = 2
 
 def run(exe, dtype, threads, env_extra=None, timeout=300):
     if not os.path.exists(exe):
-        pytest.fail(f"{exe} missing: build it in the build container (make -C integration / oracle ref)")
+        pytest.fail(f"{exe} missing: build it where the reference's sources are (make -C oracle ref)")
     env = dict(os.environ, **(env_extra or {}))
     return subprocess.run([exe, "-d", dtype, "-t", str(threads), "-i", str(ITERS)],
                           capture_output=True, text=True, timeout=timeout, env=env)

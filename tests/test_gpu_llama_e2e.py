@@ -1,5 +1,5 @@
 """BASELINE config 5 through the unchanged caller: llama.cpp-b2430's own model code and ggml
-runtime (compiled from the reference's sources by integration/Makefile), its LA_LLAMA hook
+runtime (compiled from the reference's sources by oracle/Makefile), its LA_LLAMA hook
 resolved to liblamm_hip.so, against the same driver built on the reference's own lamm opt-3
 AVX2 plug-in (oracle/Makefile llama_e2e_lamm3) -- the reference itself, run on the host.
 
@@ -27,7 +27,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, "integration", "_build", "llama_e2e_hip")
+HIP = os.path.join(ROOT, "oracle", "_ref", "llama_e2e_hip")
 CPU = os.path.join(ROOT, "oracle", "_ref", "llama_e2e_lamm3")
 SCALAR = os.path.join(ROOT, "oracle", "_ref", "llama_e2e_scalar")
 

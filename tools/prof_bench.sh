@@ -1,9 +1,11 @@
-# Full GPU test suite, the default bench line, and the rocprofv3 kernel statistics of the
-# same bench command (profiles/ copies are made by hand afterwards).  Run via gpurun.
+# Full GPU test suite, the default full bench line, and the rocprofv3 kernel statistics of the
+# same bench command (profiles/ copies are made by hand afterwards).
+# Usage: bash tools/prof_bench.sh <output dir>
 set -e
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 600 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread > gpurun_out/t_all.log 2>&1
-timeout -k 10 400 python -u bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-rm -rf gpurun_out/prof
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python3 -u bench.py --no-cpu --no-llama > gpurun_out/bench_prof.json 2> gpurun_out/bench_prof.err
+OUT=${1:?usage: bash tools/prof_bench.sh <output dir>}
+mkdir -p "$OUT"
+timeout -k 10 600 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread > "$OUT/t_all.log" 2>&1
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+rm -rf "$OUT/prof"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 -u bench.py --full --no-cpu --no-llama > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err"

@@ -11,8 +11,8 @@ OUT=${1:-gpurun_out/roofline}
 shift || true
 mkdir -p "$OUT"
 rm -rf "$OUT/kt" "$OUT/kt_idle" "$OUT/pmc_f" "$OUT/pmc_w" "$OUT/bench_prof"
-timeout -k 10 400 python3 -u bench.py --steps 20 --warmup 5 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_prof" -o run -- python3 -u bench.py --steps 20 --warmup 5 "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
+timeout -k 10 400 python3 -u bench.py --full --steps 20 --warmup 5 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_prof" -o run -- python3 -u bench.py --full --steps 20 --warmup 5 "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- python3 -u tools/roofline_trace.py > "$OUT/trace.log" 2>&1
 python3 tools/kt_roofline.py "$(find "$OUT/kt" -name '*kernel_trace.csv' | head -1)" "$OUT/roofline_q4_0_gemv_single.json"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_idle" -o run -- python3 -u tools/roofline_trace.py --sync-each --gap-us 20 > "$OUT/trace_idle.log" 2>&1
